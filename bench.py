@@ -9,6 +9,20 @@ stencils, 4 levels, 32-node subdomains, fp32 -- the configuration the north
 star's 1-GPU roofline target is quoted on.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: Allocate +
+Prepare, W warm-up applies, K timed applies, one JSON line (metric, value,
+unit, ms_per_step, ...).  --dump-outputs DIR also writes the z of the last
+timed apply, as the caller's device buffer holds it, to DIR/z.npy (float32
+[nV, 4]; above 2M vertices a fixed seeded sample of the rows; a rank of an
+N > 1 run writes its own rows, in Morton order, to DIR/z_rank<g>.npy).  The
+inputs are generated from fixed seeds, so two builds can be compared output
+for output.  Everything else described below -- the steady-state Prepare
+timings, the per-kernel and roofline passes, the sharded path's comparison
+with the unsharded apply, the PCG solves, the host-pointer path and the CPU
+baseline -- runs only with --full (the Prepare repetitions before the warm-up,
+the rest after the timed region) and adds its fields to the same JSON line.
 
 N > 1 (one rank per GPU): the same 1M problem is sharded by Morton range
 (strong scaling): rank g solves its own level-0 blocks, one RCCL allgather of
@@ -257,6 +271,20 @@ def host_path(P, mesh, contacts, r_np, make_handle, reps=5, applies=20):
                     "device-resident vectors"}
 
 
+DUMP_MAX_ROWS = 2_000_000       # float4 rows per run: 32 MB
+
+
+def dump_outputs(out_dir, name, z_np, max_rows):
+    """DIR/<name>.npy: z as float32 [n, 4]; more than max_rows rows: a fixed
+    seeded sample of them, in ascending row order."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = z_np.shape[0]
+    if n > max_rows:
+        z_np = z_np[np.sort(np.random.default_rng(0xD0).choice(n, max_rows, replace=False))]
+    np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(z_np, np.float32))
+
+
 PREP_KEYS = ("prepare_ms", "prepare_levels_ms", "prepare_assemble_ms", "prepare_factor_ms", "prepare_fine_ms",
              "prepare_complete_ms", "prepare_wall_ms")
 
@@ -362,10 +390,17 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="1M+contacts", choices=CONFIG_ORDER)
-    ap.add_argument("--cpu-steps", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pcg", action="store_true", help="skip the end-to-end PCG solve report")
-    ap.add_argument("--no-host-path", action="store_true", help="skip the host-pointer (PCIe-inclusive) report")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the z of the last timed step to DIR/z.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the steady-state Prepare timings, the per-kernel and "
+                         "roofline passes, the sharded path's check, the PCG solves, the host-pointer path and "
+                         "the CPU baseline")
+    ap.add_argument("--cpu-steps", type=int, default=20, help="--full: applies of the CPU baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-pcg", action="store_true", help="--full: skip the end-to-end PCG solve report")
+    ap.add_argument("--no-host-path", action="store_true",
+                    help="--full: skip the host-pointer (PCIe-inclusive) report")
     ap.add_argument("--sharded", action="store_true",
                     help="use the Morton-range sharded apply even on one GPU (overhead measurement)")
     ap.add_argument("--graph", action="store_true",
@@ -441,9 +476,14 @@ def main():
     # allgather of the coarse-row segments + mas_prepare_shard_complete; its
     # prepare_ms here is the two device parts, prepare_wall_ms the host wall
     # clock of all three (the collective included)
-    from mas_amd.distributed import exchange_coarse_rows
+    # A plain run keeps the Prepare of from_mesh (a sharded one still needs its
+    # coarse-row exchange, once); the repetitions are --full's
     reps = []
-    for _ in range(9):
+    if sharded_path:
+        from mas_amd.distributed import exchange_coarse_rows
+        if not args.full:
+            exchange_coarse_rows(P, None, torch.device("cuda", local))
+    for _ in range(9 if args.full else 0):
         if dist is not None:
             dist.barrier()
         t = time.perf_counter()
@@ -460,7 +500,7 @@ def main():
         if exchanged:
             stp["prepare_ms"] = stp["prepare_ms"] + stp["prepare_complete_ms"]
         reps.append(stp)
-    st0 = sorted(reps, key=lambda d: d["prepare_ms"])[len(reps) // 2]  # the median of 9
+    st0 = sorted(reps, key=lambda d: d["prepare_ms"])[len(reps) // 2] if reps else None  # the median of 9
     seed = 0x5EED + CONFIG_ORDER.index(args.config)
     r_np = meshgen.residual(mesh.nV, seed)
     r = torch.from_numpy(r_np).cuda()
@@ -522,6 +562,81 @@ def main():
     wall = time.perf_counter() - w0
     elapsed = ev0.elapsed_time(ev1) / 1e3
 
+    if args.dump_outputs:  # what the last timed step left in the caller's z
+        if world == 1:
+            dump_outputs(args.dump_outputs, "z", z.cpu().numpy(), DUMP_MAX_ROWS)
+        else:  # a rank's apply writes its own vertices only
+            own_np = P.maps()["s2o"][plan["vert_begin"]:plan["vert_end"]].astype(np.int64)
+            dump_outputs(args.dump_outputs, f"z_rank{rank}", z.cpu().numpy()[own_np], DUMP_MAX_ROWS // world)
+
+    t_max = elapsed
+    if dist is not None:
+        tt = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        t_max = float(tt.item())
+    value = args.steps / t_max          # applies of the whole problem per second
+    ms_per_step = t_max / args.steps * 1e3
+
+    out = {
+        "metric": METRIC,
+        "value": round(value, 2),
+        "unit": "applies/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 5),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {
+            "workload": {
+                "10k": "10k-vertex cloth (100x100 grid), 1 level",
+                "256k": "256k-vertex cloth (512x512 grid), 3 levels",
+                "1M+contacts": "1M-vertex cloth (1024x1024 grid) + 100k VF contact stencils, 4 levels",
+                "1M": "1M-vertex cloth (1024x1024 grid), 4 levels",
+                "4M-tet": "4M-vertex tet lattice (160^3, valence 14), 4 levels",
+            }[args.config],
+            "name": args.config,
+            "num_verts": info["num_verts"],
+            "levels": info["num_levels"],
+            "subdomain": 32,
+            "blocks": info["num_blocks"],
+            "fine_blocks": info["num_fine_blocks"],
+            "contact_stencils": info["num_stencils"],
+            "parallelism": (f"{world} Morton-range shards, allgather of level-1 segments via "
+                            + ("the library's RCCL communicator (mas_shard_apply_rccl)" if transport == "rccl"
+                               else f"a torch.distributed {args.dist_backend} hook (mas_shard_apply_device)")
+                            + (", HIP-graph replay" if use_graph else ", eager launches")
+                            if sharded_path else "single-gpu"),
+        },
+        "prepare_first_call_ms": round(st_first["prepare_ms"], 3),
+        "allocate_ms": round(st_first["allocate_ms"], 3),
+        "host_setup_s": round(setup_s, 2),
+        "wall_s_timed": round(wall, 4),
+    }
+    if args.full:
+        out.update(full_report(args, locals()))
+
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def full_report(args, env):
+    """--full: the rest of the JSON line, measured after the timed region on
+    the same handle and vectors (`env`: main()'s locals)."""
+    import numpy as np
+    import torch
+    import mas_amd
+    (P, z, r, r_np, mesh, cfg, contacts, info, plan, dist, stream, sptr, step, st0, rank, world, local,
+     sharded_path, use_graph, t_max) = (env[k] for k in (
+         "P", "z", "r", "r_np", "mesh", "cfg", "contacts", "info", "plan", "dist", "stream", "sptr", "step", "st0",
+         "rank", "world", "local", "sharded_path", "use_graph", "t_max"))
+    sharded = env.get("sharded")
+
     # kernel-duration pass: the same K applies with the library's HIP events
     # recorded on the apply stream around each kernel group (roofline source).
     if use_graph:
@@ -543,12 +658,8 @@ def main():
     coarse_b2b_ms = (P.profile_coarse(r, args.steps, sptr)
                      if not sharded_path and info["num_levels"] >= 2 else None)
 
-    t_max = elapsed
     shard_check = None
     if dist is not None:
-        tt = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        t_max = float(tt.item())
         # correctness of the sharded path on this run: every rank's own z
         # entries must equal the unsharded apply's bitwise (no communication
         # needed: each rank checks its own slice, then one MIN over ranks)
@@ -587,43 +698,8 @@ def main():
     traffic = pmc_traffic("k_solve_fine") if plan is None else (None, None, {})
     fine_s = (fine_b2b_ms if fine_b2b_ms is not None else st["fine_ms_avg"]) / 1e3
     achieved = fine_bytes / fine_s / 1e9 if fine_s > 0 else None
-    value = args.steps / t_max          # applies of the whole problem per second
-    ms_per_step = t_max / args.steps * 1e3
 
     out = {
-        "metric": METRIC,
-        "value": round(value, 2),
-        "unit": "applies/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 5),
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {
-            "workload": {
-                "10k": "10k-vertex cloth (100x100 grid), 1 level",
-                "256k": "256k-vertex cloth (512x512 grid), 3 levels",
-                "1M+contacts": "1M-vertex cloth (1024x1024 grid) + 100k VF contact stencils, 4 levels",
-                "1M": "1M-vertex cloth (1024x1024 grid), 4 levels",
-                "4M-tet": "4M-vertex tet lattice (160^3, valence 14), 4 levels",
-            }[args.config],
-            "name": args.config,
-            "num_verts": info["num_verts"],
-            "levels": info["num_levels"],
-            "subdomain": 32,
-            "blocks": info["num_blocks"],
-            "fine_blocks": info["num_fine_blocks"],
-            "contact_stencils": info["num_stencils"],
-            "parallelism": (f"{world} Morton-range shards, allgather of level-1 segments via "
-                            + ("the library's RCCL communicator (mas_shard_apply_rccl)" if transport == "rccl"
-                               else f"a torch.distributed {args.dist_backend} hook (mas_shard_apply_device)")
-                            + (", HIP-graph replay" if use_graph else ", eager launches")
-                            if sharded_path else "single-gpu"),
-        },
         "roofline": {
             "bound": "hbm",
             "kernel": "k_solve_fine (fused gather + level-0 block solves + prolongation)",
@@ -664,7 +740,6 @@ def main():
                           f"(coarse_split {st0.get('coarse_split')}), + mas_prepare_shard_complete; the coarse-row "
                           f"allgather is in prepare_wall_ms only" if sharded_path else "whole problem"),
         "prepare_wall_ms": round(st0["prepare_wall_ms"], 3),
-        "prepare_first_call_ms": round(st_first["prepare_ms"], 3),
         "prepare_breakdown_ms": {"levels": round(st0["prepare_levels_ms"], 3),
                                  "assemble": round(st0["prepare_assemble_ms"], 3),
                                  "factor": round(st0["prepare_factor_ms"], 3),
@@ -675,9 +750,6 @@ def main():
         # the handle's mas_config switches (include/mas_capi.h): 0 = the tolerance-mode defaults (z within
         # 1e-5 of the reference arithmetic), 1 = the reference's own operation order, bitwise
         "mas_config": {"reference_formation": 0, "reference_restriction": 0},
-        "allocate_ms": round(st0["allocate_ms"], 3),
-        "host_setup_s": round(setup_s, 2),
-        "wall_s_timed": round(wall, 4),
         "cpu_baseline": None,
     }
     if shard_check is not None:
@@ -728,10 +800,7 @@ def main():
         except Exception as e:  # the baseline is reported, never required
             log(f"cpu_baseline failed: {e!r}")
 
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if dist is not None:
-        dist.destroy_process_group()
+    return out
 
 
 if __name__ == "__main__":

@@ -11,7 +11,7 @@ K=()
 cd $R && \
 timeout -k 10 1000 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread "${K[@]}" > $O/pytest_gpu.log 2>&1 && \
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 && \
-timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err
 rc=$?
 tail -3 $O/pytest_gpu.log
 echo "exit $rc"
