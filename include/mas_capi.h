@@ -56,7 +56,9 @@ extern "C" {
  *    mas_set_prepare_allgather; mas_stats.prepare_complete_ms and coarse_split
  *    from the reserved tail, same size); mas_allgather_loopback;
  *    mas_config.host_register (from the reserved tail, same size): opt-in
- *    page-locking of the caller's host arrays. */
+ *    page-locking of the caller's host arrays.
+ *    mas_config.wide_inverse (from the reserved tail, same size, same version:
+ *    0 keeps meaning the default). */
 #define MAS_ABI_VERSION 5
 
 typedef enum {
@@ -114,7 +116,13 @@ typedef struct {
                           with its allocation covering its last page whole (posix_memalign /
                           mmap rounded to pages); an array that does not start on a page is
                           never registered (its pages may be shared with other allocations) */
-    int reserved[7];
+    int wide_inverse;  /* from the reserved tail, same size.  0 = Prepare also writes a 24-bit copy of the
+                          level-0 inverses (one fp32 scale per 72-entry lane record, 14 272 B per block
+                          against 18 624 B; +77 % of the level-0 inverse bytes in device memory) and
+                          the apply streams that copy: z within 1e-6 of the fp32 apply (DESIGN.md
+                          section 4); 1 = no such copy, the apply reads the fp32 inverses.  The getters
+                          and the blob always hold the fp32 inverses.  Env MAS_INV_WIDE overrides */
+    int reserved[6];
 } mas_config;
 
 typedef struct {

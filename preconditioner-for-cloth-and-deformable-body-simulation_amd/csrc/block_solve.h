@@ -5,6 +5,7 @@
 
 #include "layout.h"
 #include "mas_internal.h"
+#include "narrow.h"
 
 namespace mas {
 
@@ -85,6 +86,46 @@ __device__ __forceinline__ void load_record(const float4* __restrict__ inv, int 
         g[4 * q + 3] = x.w;
     }
     const float* t = reinterpret_cast<const float*>(inv + (size_t)blk * kBlockF4) + kMainFloats + 3 * (lane & 15);
+    tl[0] = t[0];
+    tl[1] = t[1];
+    tl[2] = t[2];
+    if (lane >= 16) tl[0] = tl[1] = tl[2] = 0.f;
+}
+
+// The same registers from the 24-bit copy of a level-0 block (narrow.h): 13
+// dwordx4 and one dwordx2 per lane, the lane's scale, the fp32 tail; every
+// entry decoded as float(q) * s, so block_solve runs unchanged.
+template <bool NT = false>
+__device__ __forceinline__ void load_record_narrow(const void* __restrict__ invN, int blk, int lane,
+                                                   float (&g)[kRecord], float (&tl)[3]) {
+    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    typedef uint32_t v2u __attribute__((ext_vector_type(2)));
+    const char* b = static_cast<const char*>(invN) + (size_t)blk * kNarrowBlockBytes;
+    uint32_t w[kNarrowDwords];
+#pragma unroll
+    for (int q = 0; q < kNarrowGroups; ++q) {
+        const v4u* bp = reinterpret_cast<const v4u*>(b) + q * 64 + lane;
+        const v4u x = NT ? __builtin_nontemporal_load(bp) : *bp;
+        w[4 * q + 0] = x.x;
+        w[4 * q + 1] = x.y;
+        w[4 * q + 2] = x.z;
+        w[4 * q + 3] = x.w;
+    }
+    {
+        const v2u* bp = reinterpret_cast<const v2u*>(b + kNarrowLastOff) + lane;
+        const v2u x = NT ? __builtin_nontemporal_load(bp) : *bp;
+        w[52] = x.x;
+        w[53] = x.y;
+    }
+    const float s = reinterpret_cast<const float*>(b + kNarrowScaleOff)[lane];
+#pragma unroll
+    for (int t = 0; t < kRecord / 4; ++t) {
+        int q[4];
+        narrow_unpack4(w[3 * t], w[3 * t + 1], w[3 * t + 2], q);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) g[4 * t + c] = narrow_decode(q[c], s);
+    }
+    const float* t = reinterpret_cast<const float*>(b + kNarrowTailOff) + 3 * (lane & 15);
     tl[0] = t[0];
     tl[1] = t[1];
     tl[2] = t[2];

@@ -16,8 +16,10 @@
 //   k_solve_fine        every level-0 block fused with the gather r[s2o[v]]
 //                       and the prolongation z[s2o[v]] = Z0 + Z1[a1] + Z2[a2]
 //                       + Z3[a3] (CollectFinalZ .cpp:1698-1719, min(L,4)-1
-//                       coarse levels, B-6).  This kernel streams 18 624 B of
-//                       packed inverse per block and dominates the apply.
+//                       coarse levels, B-6).  This kernel streams each
+//                       block's packed inverse -- by default its 24-bit copy,
+//                       14 272 B (narrow.h), else the 18 624 B of fp32 -- and
+//                       dominates the apply.
 //
 // Block solve (layout.h): one wave64 per 32-node block, lane 32h + n owns
 // node n; the halves split the 3x3 node-pair blocks by rotation distance.
@@ -55,8 +57,13 @@ __device__ __forceinline__ int xcd_chunked(int g, int G) {
     return g < full ? (g & 7) * (full >> 3) + (g >> 3) : g;
 }
 
-template <int NPROL, int VAR, bool RZ, int WPB = kApplyThreads / 64>
-__device__ __forceinline__ void solve_fine_body(const float4* __restrict__ inv, int blk0, int nFineBlk, int nV,
+// NARROW: inv is the 24-bit copy of the level-0 inverses (narrow.h), decoded
+// into the same registers; everything after the load is shared.  The forms the
+// library takes by default have it (VAR 4 / 8 in two-wave workgroups, their RZ
+// forms, so launch_fine_z0 and the MAS_RESIDENT_SPLIT launches too); the A/B
+// variants 0, 1, 3, 4, 5, 7 keep reading the fp32 inverses.
+template <int NPROL, int VAR, bool RZ, int WPB = kApplyThreads / 64, bool NARROW = false>
+__device__ __forceinline__ void solve_fine_body(const void* __restrict__ inv, int blk0, int nFineBlk, int nV,
                                                 const float4* __restrict__ r, const int4* __restrict__ vmap,
                                                 const float4* __restrict__ zc, int begin1, float4* __restrict__ z,
                                                 double* __restrict__ rzPart) {
@@ -68,7 +75,8 @@ __device__ __forceinline__ void solve_fine_body(const float4* __restrict__ inv, 
     const bool vvalid = bvalid && v < nV;
     const int4 m = vmap[vvalid ? v : 0];
     float g[kRecord], tl[3];
-    load_record<VAR != 0 && VAR != 8>(inv, bvalid ? blk : 0, lane, g, tl);
+    if (NARROW) load_record_narrow<VAR != 0 && VAR != 8>(inv, bvalid ? blk : 0, lane, g, tl);
+    else load_record<VAR != 0 && VAR != 8>(static_cast<const float4*>(inv), bvalid ? blk : 0, lane, g, tl);
     const float4 rv = r[m.x];
     const float3 rr = vvalid ? make_float3(rv.x, rv.y, rv.z) : make_float3(0.f, 0.f, 0.f);
     float3 out = block_solve(g, tl, rr, lane);
@@ -108,15 +116,15 @@ __device__ __forceinline__ void solve_fine_body(const float4* __restrict__ inv, 
 // bitwise equal (profiles/round4/ab/fine_wpb/): 1M + contacts 113.0 -> 112.0
 // us per apply, 256k 32.03 -> 31.78, 4M tet 453.6 -> 451.3 (one-wave
 // workgroups: better at 1M, worse at 256k and 4M).
-template <int NPROL, int VAR, bool RZ, int WPB = kApplyThreads / 64>
-__global__ __launch_bounds__(64 * WPB) void k_solve_fine(const float4* __restrict__ inv, int blk0, int nFineBlk,
+template <int NPROL, int VAR, bool RZ, int WPB = kApplyThreads / 64, bool NARROW = false>
+__global__ __launch_bounds__(64 * WPB) void k_solve_fine(const void* __restrict__ inv, int blk0, int nFineBlk,
                                                         int nV, const float4* __restrict__ r,
                                                         const int4* __restrict__ vmap,
                                                         const float4* __restrict__ zc, int begin1,
                                                         float4* __restrict__ z, const int* __restrict__ done,
                                                         double* __restrict__ rzPart) {
     if (RZ && *done) return;
-    solve_fine_body<NPROL, VAR, RZ, WPB>(inv, blk0, nFineBlk, nV, r, vmap, zc, begin1, z, rzPart);
+    solve_fine_body<NPROL, VAR, RZ, WPB, NARROW>(inv, blk0, nFineBlk, nV, r, vmap, zc, begin1, z, rzPart);
 }
 
 // A/B (MAS_FINE_VARIANT=7): the chunked form in one-wave workgroups.
@@ -273,10 +281,43 @@ __global__ __launch_bounds__(256) void k_members(int nChild, int childBegin, con
 }
 
 
+// the default forms (var 6 / 8) reading the 24-bit copy invN
 template <int NPROL>
-static void launch_fine_n(int var, int g, hipStream_t s, const float4* inv, int blk0, int blkEnd, int nV,
-                          const float4* r, const int4* vmap, const float4* zc, int begin1, float4* z,
+static void launch_fine_narrow(int var, hipStream_t s, const void* invN, int blk0, int blkEnd, int nV,
+                               const float4* r, const int4* vmap, const float4* zc, int begin1, float4* z,
+                               const int* done, double* rzPart, int rzWpb) {
+    const int nb = blkEnd - blk0;
+    if (rzPart) {
+        if (var == 6 && rzWpb == 8)
+            k_solve_fine<NPROL, 4, true, 8, true><<<cdiv(nb, 8), 512, 0, s>>>(invN, blk0, blkEnd, nV, r, vmap, zc,
+                                                                            begin1, z, done, rzPart);
+        else if (var == 6 && rzWpb == 4)
+            k_solve_fine<NPROL, 4, true, 4, true><<<cdiv(nb, 4), 256, 0, s>>>(invN, blk0, blkEnd, nV, r, vmap, zc,
+                                                                            begin1, z, done, rzPart);
+        else if (var == 8)
+            k_solve_fine<NPROL, 8, true, 4, true><<<cdiv(nb, 4), 256, 0, s>>>(invN, blk0, blkEnd, nV, r, vmap, zc,
+                                                                            begin1, z, done, rzPart);
+        else
+            k_solve_fine<NPROL, 4, true, 2, true><<<cdiv(nb, 2), 128, 0, s>>>(invN, blk0, blkEnd, nV, r, vmap, zc,
+                                                                            begin1, z, done, rzPart);
+    } else if (var == 8) {
+        k_solve_fine<NPROL, 8, false, 2, true><<<cdiv(nb, 2), 128, 0, s>>>(invN, blk0, blkEnd, nV, r, vmap, zc,
+                                                                         begin1, z, nullptr, nullptr);
+    } else {
+        k_solve_fine<NPROL, 4, false, 2, true><<<cdiv(nb, 2), 128, 0, s>>>(invN, blk0, blkEnd, nV, r, vmap, zc,
+                                                                         begin1, z, nullptr, nullptr);
+    }
+}
+
+// invN (not null): the 24-bit copy, read by the default forms
+template <int NPROL>
+static void launch_fine_n(int var, int g, hipStream_t s, const float4* inv, const void* invN, int blk0, int blkEnd,
+                          int nV, const float4* r, const int4* vmap, const float4* zc, int begin1, float4* z,
                           const int* done, double* rzPart, int rzWpb = 2) {
+    if (invN && (var == 6 || var == 8)) {
+        launch_fine_narrow<NPROL>(var, s, invN, blk0, blkEnd, nV, r, vmap, zc, begin1, z, done, rzPart, rzWpb);
+        return;
+    }
     if (rzPart) {  // the PCG driver's applies (fine_grid(h) workgroups: one r.z partial each)
         if (var == 6 && rzWpb == 8)
             k_solve_fine<NPROL, 4, true, 8><<<cdiv(blkEnd - blk0, 8), 512, 0, s>>>(inv, blk0, blkEnd, nV, r, vmap, zc,
@@ -328,10 +369,12 @@ static void launch_fine_n(int var, int g, hipStream_t s, const float4* inv, int 
 // default-policy loads (8) let the Infinity Cache keep them from one apply to
 // the next: 256k 31.35 -> 30.51 us per apply, PCG 0.0753 -> 0.0729
 // ms/iteration; 1M 110.9 -> 125.1 us (profiles/round5/ab/fine_inv_policy/).
-// Bitwise equal.  MAS_INV_RESIDENT=0/1 forces either.
+// Bitwise equal.  MAS_INV_RESIDENT=0/1 forces either.  The bytes counted are
+// those of the copy the launch reads: the 24-bit one (narrow.h, 14 272 B per
+// block) unless wide_inverse.
 static int fine_var(const mas_context* h, int nb) {
     if (h->fineVariant != 6) return h->fineVariant;
-    const size_t bytes = (size_t)nb * (kBlockFloats * 4 + 32 * 48);
+    const size_t bytes = (size_t)nb * ((h->wideInverse ? kBlockFloats * 4 : kNarrowBlockBytes) + 32 * 48);
     const bool resident = h->invResident >= 0 ? h->invResident != 0 : bytes <= ((size_t)192 << 20);
     return resident ? 8 : 6;
 }
@@ -344,6 +387,7 @@ void launch_fine(mas_context* h, int blk0, int blkEnd, const float4* r, float4* 
     const int g = cdiv(blkEnd - blk0, kApplyThreads / 64);
     if (g <= 0) return;
     const float4* inv = P<float4>(h->inv);
+    const void* invN = narrow_inv(h);  // null with wide_inverse
     const int4* vmap = P<int4>(h->vmap);
     const float4* zc = P<float4>(h->Zc);
     const int begin1 = h->levelSize[3], nV = h->nV, var = fine_var(h, blkEnd - blk0);
@@ -351,10 +395,10 @@ void launch_fine(mas_context* h, int blk0, int blkEnd, const float4* r, float4* 
     auto go = [&](int v, int b0, int b1) {
         const int gg = cdiv(b1 - b0, kApplyThreads / 64);
         switch (L < 4 ? L - 1 : 3) {
-            case 0: launch_fine_n<0>(v, gg, s, inv, b0, b1, nV, r, vmap, zc, begin1, z, done, rzPart, w); break;
-            case 1: launch_fine_n<1>(v, gg, s, inv, b0, b1, nV, r, vmap, zc, begin1, z, done, rzPart, w); break;
-            case 2: launch_fine_n<2>(v, gg, s, inv, b0, b1, nV, r, vmap, zc, begin1, z, done, rzPart, w); break;
-            default: launch_fine_n<3>(v, gg, s, inv, b0, b1, nV, r, vmap, zc, begin1, z, done, rzPart, w); break;
+            case 0: launch_fine_n<0>(v, gg, s, inv, invN, b0, b1, nV, r, vmap, zc, begin1, z, done, rzPart, w); break;
+            case 1: launch_fine_n<1>(v, gg, s, inv, invN, b0, b1, nV, r, vmap, zc, begin1, z, done, rzPart, w); break;
+            case 2: launch_fine_n<2>(v, gg, s, inv, invN, b0, b1, nV, r, vmap, zc, begin1, z, done, rzPart, w); break;
+            default: launch_fine_n<3>(v, gg, s, inv, invN, b0, b1, nV, r, vmap, zc, begin1, z, done, rzPart, w); break;
         }
     };
     // A/B (env MAS_RESIDENT_SPLIT = K): the first K blocks' inverses with
@@ -442,8 +486,8 @@ void launch_prolong(mas_context* h, int v0, int v1, float4* z, hipStream_t s) {
 void launch_fine_z0(mas_context* h, int blk0, int blkEnd, const float4* r, float4* z, hipStream_t s) {
     const int g = cdiv(blkEnd - blk0, kApplyThreads / 64);
     if (g <= 0) return;
-    launch_fine_n<0>(fine_var(h, blkEnd - blk0), g, s, P<float4>(h->inv), blk0, blkEnd, h->nV, r, P<int4>(h->vmap),
-                     P<float4>(h->Zc), h->levelSize[3], z, nullptr, nullptr);
+    launch_fine_n<0>(fine_var(h, blkEnd - blk0), g, s, P<float4>(h->inv), narrow_inv(h), blk0, blkEnd, h->nV, r,
+                     P<int4>(h->vmap), P<float4>(h->Zc), h->levelSize[3], z, nullptr, nullptr);
 }
 
 // the coarse form an apply uses: the env / config choice, else the one-launch

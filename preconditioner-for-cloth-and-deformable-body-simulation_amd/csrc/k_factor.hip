@@ -25,6 +25,7 @@
 
 #include "layout.h"
 #include "mas_internal.h"
+#include "narrow.h"
 
 namespace mas {
 
@@ -682,6 +683,54 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
 // workgroup barrier per step -- was bitwise equal but slower, 2.18 -> 2.75 ms
 // at 1M + contacts: LDS and VGPRs already allow 8 blocks per CU either way,
 // so it only added a barrier to every step; profiles/round5/ab/.)
+// The 24-bit copy of level-0 blocks [b0, b1) (narrow.h) from their fp32
+// inverses: one wave per block, lane L encodes its own record (the 18 float4
+// the apply would load) in registers and stores 13 uint4 + one uint2, its
+// scale, and lanes 0..11 copy the fp32 tail.  Launched behind every writer of
+// level-0 inverses on that writer's stream, so the copy is never stale: right
+// behind each chunk of the fused factor, whose 8 192 blocks (153 MB at 1M) are
+// still in the Infinity Cache.
+__global__ __launch_bounds__(256) void k_narrow_inv(const float4* __restrict__ inv, char* __restrict__ out, int b0,
+                                                    int b1) {
+    const int blk = b0 + blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (blk >= b1) return;  // wave-uniform
+    const int lane = threadIdx.x & 63;
+    const float4* src = inv + (size_t)blk * kBlockF4;
+    float x[kRecord];
+#pragma unroll
+    for (int q = 0; q < kRecord / 4; ++q) {
+        const float4 v = src[q * 64 + lane];
+        x[4 * q + 0] = v.x;
+        x[4 * q + 1] = v.y;
+        x[4 * q + 2] = v.z;
+        x[4 * q + 3] = v.w;
+    }
+    uint32_t w[kNarrowDwords];
+    float sc;
+    narrow_encode_record(x, w, sc);
+    char* dst = out + (size_t)blk * kNarrowBlockBytes;
+#pragma unroll
+    for (int g = 0; g < kNarrowGroups; ++g)
+        reinterpret_cast<uint4*>(dst)[g * 64 + lane] = make_uint4(w[4 * g], w[4 * g + 1], w[4 * g + 2], w[4 * g + 3]);
+    reinterpret_cast<uint2*>(dst + kNarrowLastOff)[lane] = make_uint2(w[52], w[53]);
+    reinterpret_cast<float*>(dst + kNarrowScaleOff)[lane] = sc;
+    if (lane < 12) reinterpret_cast<float4*>(dst + kNarrowTailOff)[lane] = src[kMainFloats / 4 + lane];
+}
+
+int ensure_narrow(mas_context* h) {
+    if (h->wideInverse) return MAS_OK;
+    return ensure(h, h->invNarrow, (size_t)(h->nFineBlk > 0 ? h->nFineBlk : 1) * kNarrowBlockBytes);
+}
+
+int narrow_blocks(mas_context* h, int b0, int b1, hipStream_t s) {
+    if (b1 > h->nFineBlk) b1 = h->nFineBlk;  // coarse blocks stay fp32
+    if (h->wideInverse || b1 <= b0) return MAS_OK;
+    if (h->invNarrow.bytes < (size_t)h->nFineBlk * kNarrowBlockBytes)
+        return fail(h, MAS_ERR_STATE, "the 24-bit inverse copy was not allocated");
+    k_narrow_inv<<<cdiv(b1 - b0, 4), 256, 0, s>>>(P<float4>(h->inv), P<char>(h->invNarrow), b0, b1);
+    return hip_check(h, hipGetLastError(), "narrow inverse kernel");
+}
+
 int launch_factor_fused(mas_context* h, const FineAsm& a, int blk0, int blk1, hipStream_t s) {
     // The blocks in C launches in a row (round 6): between two of them the
     // queue waits for the earlier one to drain, and the coarse assembly's
@@ -710,6 +759,7 @@ int launch_factor_fused(mas_context* h, const FineAsm& a, int blk0, int blk1, hi
         else if (b1 > b0)
             k_factor_fused<false><<<b1 - b0, 64, 0, s>>>(a, P<float>(h->inv), P<uint4>(h->tileSlot),
                                                          P<uint4>(h->valuSlot), b0, P<int>(h->devStatus));
+        if (int rc = narrow_blocks(h, b0, b1, s)) return rc;
     }
     return hip_check(h, hipGetLastError(), "fused factor kernel");
 }
@@ -788,7 +838,8 @@ int factor_blocks(mas_context* h, int b0, int b1, hipStream_t s) {
             k_factor_rb<false><<<nb, 64, 0, s>>>(dense, inv, P<uint4>(h->tileSlot), P<uint4>(h->valuSlot), b0,
                                                  P<int>(h->devStatus));
     }
-    return hip_check(h, hipGetLastError(), "factor kernel");
+    if (int rc = hip_check(h, hipGetLastError(), "factor kernel")) return rc;
+    return narrow_blocks(h, b0, b1, s);  // its level-0 blocks, if any
 }
 
 int run_factor(mas_context* h, hipStream_t s) {

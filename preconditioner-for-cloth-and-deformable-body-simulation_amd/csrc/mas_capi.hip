@@ -186,6 +186,8 @@ int mas_create(mas_handle* out, const mas_config* cfg) {
     }
     if (const char* v = std::getenv("MAS_FINE_VARIANT")) h->fineVariant = std::atoi(v);
     if (const char* v = std::getenv("MAS_INV_RESIDENT")) h->invResident = std::atoi(v) != 0;
+    h->wideInverse = h->cfg.wide_inverse != 0;
+    if (const char* v = std::getenv("MAS_INV_WIDE")) h->wideInverse = std::atoi(v) != 0;
     if (const char* v = std::getenv("MAS_RESIDENT_SPLIT")) h->residentSplit = std::atoi(v);
     if (const char* v = std::getenv("MAS_COARSE_OCC")) h->coarseOcc = std::atoi(v);
     if (const char* v = std::getenv("MAS_COARSE_NARROW")) h->coarseNarrow = std::atoi(v);

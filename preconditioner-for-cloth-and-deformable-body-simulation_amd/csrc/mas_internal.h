@@ -10,6 +10,9 @@
 //     apply kernel needs about a vertex in one 16-byte load.
 //   * inv: per block 4656 fp32 (18 624 B, the reference's packed size) in the
 //     node-pair-rotation layout described in layout.h.
+//   * invNarrow: the level-0 blocks of inv again as 24-bit scaled records
+//     (14 272 B per block, narrow.h): what the fine apply kernel streams
+//     unless wide_inverse.
 //   * Rc / Zc: coarse residual / solution, float4 per node id >= begin_1.
 #pragma once
 
@@ -218,6 +221,11 @@ struct mas_context {
     // loads (A/B)
     int fineVariant = 6;
     int residentSplit = 0;  // env MAS_RESIDENT_SPLIT (A/B, launch_fine): first K blocks default-policy
+    // 0 (default): Prepare also writes the 24-bit copy of the level-0 inverses
+    // (invNarrow, narrow.h) and the fine kernel's default forms stream it;
+    // 1 (mas_config.wide_inverse, env MAS_INV_WIDE): no such copy, the fine
+    // kernel reads the fp32 inverses
+    int wideInverse = 0;
     int invResident = -1;  // env MAS_INV_RESIDENT: -1 by size (fine_var, k_apply.hip), 0 / 1 forced
     // blocks (waves) per workgroup of the fine kernel in the PCG's applies,
     // one r.z partial per workgroup, summed by every SpMV workgroup (env
@@ -269,6 +277,7 @@ struct mas_context {
     // unless level-0 blocks are kept (cfg.keep_blocks or an unfused factor
     // variant); denseBase = the address block 0 would have (dense_base()).
     mas::Buffer dense, inv, slotTable, tileSlot, valuSlot;
+    mas::Buffer invNarrow;  // nFineBlk narrow blocks (narrow.h), rewritten after every writer of level-0 inverses
     bool denseFine = false;  // the last Prepare stored the level-0 blocks
     hipStream_t prepStream = nullptr;  // fused level-0 assemble + factor, beside the coarse assembly
     hipEvent_t evPrepFork = nullptr, evPrepJoin = nullptr;
@@ -440,7 +449,7 @@ struct mas_context {
         mas::Buffer* all[] = {&pos, &starts, &idx, &edges, &faces, &morton, &mortonSorted, &iota, &s2o, &o2s,
                               &nbrNum, &nbr, &nbrNumRem, &nbrRem, &aabbPartial, &rawContacts, &stencilFlags,
                               &stencilSlots, &stencils, &fineMask, &nextMask, &bankCount, &bankPrefix, &levelTotal,
-                              &cst, &goingNext, &vmap, &coarseTables, &dense, &inv, &slotTable, &tileSlot, &valuSlot, &additional, &od,
+                              &cst, &goingNext, &vmap, &coarseTables, &dense, &inv, &invNarrow, &slotTable, &tileSlot, &valuSlot, &additional, &od,
                               &recCnt, &recOff, &rec, &recKeys, &recKeysSorted, &recIds, &recIdsSorted, &vkeys,
                               &tab, &termCnt,
                               &cdCnt, &cdOff, &cdKeys, &cdKeysS, &cdIds, &cdIdsS, &cdVal, &cFineOff, &cdEnt, &c0Ent, &caCnt, &caOff,
@@ -481,6 +490,13 @@ inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 inline float* dense_base(mas_context* h) {
     return P<float>(h->dense) - (h->denseFine ? 0 : (ptrdiff_t)h->nFineBlk * kDenseFloats);
 }
+
+// the 24-bit copy the fine kernel reads (null with wide_inverse: it reads inv)
+inline const void* narrow_inv(const mas_context* h) { return h->wideInverse ? nullptr : h->invNarrow.p; }
+// room for it (no-op with wide_inverse); narrow_blocks rewrites the level-0
+// blocks of [b0, b1) from inv on s (k_factor.hip)
+int ensure_narrow(mas_context* h);
+int narrow_blocks(mas_context* h, int b0, int b1, hipStream_t s);
 
 // phase entry points (host orchestration), defined per translation unit
 int run_allocate(mas_context* h, const float* pos4, const int* starts, const int* idx, const int* edges4,

@@ -42,6 +42,9 @@ int run_prepare(mas_context* h, const float* d_diag9, const float* d_off9, const
     h->nFineBlk = ceil32(h->nV) / 32;
     h->fineBlk0 = (int)((long long)h->prepRank * h->nFineBlk / h->prepWorld);
     h->fineBlk1 = (int)((long long)(h->prepRank + 1) * h->nFineBlk / h->prepWorld);
+    // the 24-bit copy of the level-0 inverses: sized here, on this thread,
+    // before any factor (the early path's worker included) can write it
+    if ((rc = ensure_narrow(h))) return rc;
     // fused variants: the level-0 contacts and the fused kernel start on
     // prepStream after the stencils (the fork event), beside the level build;
     // their launches are queued while the level kernels run (run_levels' hook)
