@@ -166,6 +166,15 @@ class SeSchwarzPreconditioner {
     //==== MI355X extensions
     // z and residual are device pointers (hipMalloc'd float4[nV]); stream is a hipStream_t.
     void PreconditioningDevice(SeVec3fSimd* z, const SeVec3fSimd* residual, void* stream = nullptr);
+    // count (1 .. MAS_MAX_RHS) residuals through one pass over the inverses
+    // (mas_apply_multi / mas_apply_multi_device): z[k] is bitwise what
+    // Preconditioning(z[k], residual[k]) writes.  z and residual are host arrays
+    // of count pointers: to host vectors (Multi; dim unused) or to device
+    // vectors (DeviceMulti).  The z[k] are distinct from each other and from
+    // every residual[j].
+    void PreconditioningMulti(SeVec3fSimd* const* z, const SeVec3fSimd* const* residual, int count, int dim);
+    void PreconditioningDeviceMulti(SeVec3fSimd* const* z, const SeVec3fSimd* const* residual, int count,
+                                    void* stream = nullptr);
     mas_handle Handle() const { return m_handle; }
 
   private:

@@ -58,7 +58,9 @@ extern "C" {
  *    mas_config.host_register (from the reserved tail, same size): opt-in
  *    page-locking of the caller's host arrays.
  *    mas_config.wide_inverse (from the reserved tail, same size, same version:
- *    0 keeps meaning the default). */
+ *    0 keeps meaning the default).
+ *    mas_apply_multi_device / mas_apply_multi and MAS_MAX_RHS (new symbols, no
+ *    layout changed: same version). */
 #define MAS_ABI_VERSION 5
 
 typedef enum {
@@ -213,6 +215,44 @@ int mas_apply(mas_handle h, float* z4, const float* r4);
 /* Preconditioning on device vectors d_z4, d_r4 ([nV][4], 16-B aligned).
  * stream: hipStream_t (NULL = handle stream).  Asynchronous. */
 int mas_apply_device(mas_handle h, float* d_z4, const float* d_r4, void* stream);
+
+/* ---- multi-vector apply: one prepared handle, up to MAS_MAX_RHS residuals ----
+ * The apply is bound by the bytes of the level-0 inverses, which do not depend
+ * on the residual: a batch reads them once per pass of up to 4 vectors instead
+ * of once per vector (block or enlarged CG, several load / adjoint vectors of
+ * one Hessian, sensitivity solves).
+ *
+ * d_z4 and d_r4 are HOST arrays of `count` device pointers, each [nV][4] fp32
+ * and 16-byte aligned; they are read during the call only (the kernels take the
+ * pointers by value: no device-side table, no copy).  A contiguous
+ * [count][nV][4] buffer is passed as strided pointers.  Asynchronous on
+ * `stream`, like mas_apply_device.
+ *
+ * For every k, z[k] is bit for bit what mas_apply_device(h, z[k], r[k]) writes
+ * on the same handle, for every level count, both inverse formats
+ * (wide_inverse) and both level-3 forms (reference_restriction).  Two entries
+ * of d_r4 may be the same vector.  MAS_ERR_ARG, before anything is queued, for
+ * count outside 1 .. MAS_MAX_RHS, a null or misaligned entry, and a z[k] that
+ * is another z[j] or any r[j]; MAS_ERR_STATE for an unprepared or a
+ * shard-prepared handle.  count == 1 is mas_apply_device.
+ *
+ * The coarse residuals / solutions of a batch live in buffers of their own, one
+ * slab per vector, grown by the first call at a given count: that call
+ * synchronises the device and must happen outside a stream capture; later
+ * calls at that count or a smaller one allocate nothing and can be captured.
+ * mas_get_coarse_residual and the single-vector applies are not affected by a
+ * batch, nor a batch by them.  Every level is its own launch, ordered by the
+ * stream alone: the path has no device-side wait, so it cannot give up
+ * (mas_stats.wait_timeouts).  mas_stats.apply_calls grows by count; the events
+ * of mas_set_profiling are not recorded on this path. */
+#define MAS_MAX_RHS 8
+int mas_apply_multi_device(mas_handle h, int count, float* const* d_z4, const float* const* d_r4, void* stream);
+/* The same with host vectors z4[k], r4[k] ([nV][4] each; z entries distinct
+ * from each other and from every r entry).  Stages through device buffers of
+ * count x nV x 16 bytes each way and is synchronous.  The copies are plain
+ * pageable ones: mas_config.host_register does not apply here, and the
+ * registrations mas_apply holds for its own r and z are left alone. */
+int mas_apply_multi(mas_handle h, int count, float* const* z4, const float* const* r4);
 
 /* ---- GPU-resident PCG, the caller of the apply ----
  * Solves A x = b with preconditioned conjugate gradients on the device, A the

@@ -11,6 +11,13 @@ namespace mas {
 
 constexpr int kApplyThreads = 256;  // 4 waves = 4 blocks per workgroup
 
+// Workgroups dealt to the XCDs in contiguous chunks (workgroup g runs on XCD
+// g % 8, so logical workgroup (g % 8) * (G / 8) + g / 8): see k_apply.hip VAR 4.
+__device__ __forceinline__ int xcd_chunked(int g, int G) {
+    const int full = G & ~7;
+    return g < full ? (g & 7) * (full >> 3) + (g >> 3) : g;
+}
+
 // One rotation step: out += G r_src, and lane dst receives G^T r_own.
 __device__ __forceinline__ void pair_step(float3& out, const float (&G)[9], float3 r, int src, int dst) {
     const float mx = __shfl(r.x, src), my = __shfl(r.y, src), mz = __shfl(r.z, src);

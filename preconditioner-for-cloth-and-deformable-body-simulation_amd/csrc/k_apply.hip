@@ -52,10 +52,7 @@ static inline int grid_for_blocks(int blocks) { return cdiv(blocks, kApplyThread
 // share an XCD's L2 for the r lines they gather and the z lines they write.
 // Interleaved in one process, bitwise equal (profiles/round4/fine_pmc/ab_*.json):
 // 4M tet 382 -> 357 us per launch, 1M + contacts 98.5 -> 98.0 us.
-__device__ __forceinline__ int xcd_chunked(int g, int G) {
-    const int full = G & ~7;
-    return g < full ? (g & 7) * (full >> 3) + (g >> 3) : g;
-}
+// (xcd_chunked: block_solve.h, shared with k_multi.hip.)
 
 // NARROW: inv is the 24-bit copy of the level-0 inverses (narrow.h), decoded
 // into the same registers; everything after the load is shared.  The forms the
@@ -371,10 +368,12 @@ static void launch_fine_n(int var, int g, hipStream_t s, const float4* inv, cons
 // ms/iteration; 1M 110.9 -> 125.1 us (profiles/round5/ab/fine_inv_policy/).
 // Bitwise equal.  MAS_INV_RESIDENT=0/1 forces either.  The bytes counted are
 // those of the copy the launch reads: the 24-bit one (narrow.h, 14 272 B per
-// block) unless wide_inverse.
-static int fine_var(const mas_context* h, int nb) {
+// block) unless wide_inverse.  nvec: the vectors the launch serves (k_multi.hip):
+// per vertex 16 B of map and 32 B of r and z per vector.
+int fine_var(const mas_context* h, int nb, int nvec) {
     if (h->fineVariant != 6) return h->fineVariant;
-    const size_t bytes = (size_t)nb * ((h->wideInverse ? kBlockFloats * 4 : kNarrowBlockBytes) + 32 * 48);
+    const size_t bytes =
+        (size_t)nb * ((h->wideInverse ? kBlockFloats * 4 : kNarrowBlockBytes) + 32 * (16 + 32 * nvec));
     const bool resident = h->invResident >= 0 ? h->invResident != 0 : bytes <= ((size_t)192 << 20);
     return resident ? 8 : 6;
 }

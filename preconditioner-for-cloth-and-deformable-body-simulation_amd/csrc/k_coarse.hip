@@ -367,12 +367,15 @@ DeepArgs deep_args(mas_context* h, const float4* src, const int* idx) {
 }
 
 // every level-3 node (L >= 4); src/idx: R1 and the list entries' positions
-// in it (null: Rc and deepIdx)
-void launch_coarse_deep(mas_context* h, const float4* src, const int* idx, hipStream_t s) {
+// in it (null: rc and deepIdx); rc / zc: the coarse R / Z the launch reads and
+// writes (null: the handle's Rc / Zc; a slab of the multi-vector apply, k_multi.hip)
+void launch_coarse_deep(mas_context* h, const float4* src, const int* idx, hipStream_t s, float4* rc, float4* zc) {
     if (h->L < 4) return;
-    const DeepArgs d = deep_args(h, src ? src : P<float4>(h->Rc), idx ? idx : P<int>(h->deepIdx));
-    k_coarse_deep<<<deep_nodes(h), kApplyThreads, 0, s>>>(P<float4>(h->inv), d, P<float4>(h->Rc), P<float4>(h->Zc),
-                                                          h->levelSize[3], h->applyDone);
+    if (!rc) rc = P<float4>(h->Rc);
+    if (!zc) zc = P<float4>(h->Zc);
+    const DeepArgs d = deep_args(h, src ? src : rc, idx ? idx : P<int>(h->deepIdx));
+    k_coarse_deep<<<deep_nodes(h), kApplyThreads, 0, s>>>(P<float4>(h->inv), d, rc, zc, h->levelSize[3],
+                                                          h->applyDone);
 }
 
 // L >= 3: k_restrict12, then k_solve123 (level-3 nodes + levels 1 and 2).

@@ -395,6 +395,72 @@ int mas_apply_device(mas_handle h, float* d_z4, const float* d_r4, void* stream)
     return run_apply(h, reinterpret_cast<float4*>(d_z4), reinterpret_cast<const float4*>(d_r4), s);
 }
 
+// the operand rules of the multi-vector applies (device or host pointers): count
+// in range, no null entry, `align`-byte alignment, no z[k] that is another z[j]
+// or any r[j] (two r entries may be one vector)
+static int check_multi(mas_handle h, const char* fn, int count, float* const* z4, const float* const* r4,
+                       uintptr_t align) {
+    const std::string name(fn);
+    if (count < 1 || count > MAS_MAX_RHS)
+        return fail(h, MAS_ERR_ARG, name + ": count must be 1 .. " + std::to_string(MAS_MAX_RHS));
+    if (!z4 || !r4) return fail(h, MAS_ERR_ARG, name + ": null pointer array");
+    for (int k = 0; k < count; ++k) {
+        if (!z4[k] || !r4[k]) return fail(h, MAS_ERR_ARG, name + ": null vector " + std::to_string(k));
+        if ((reinterpret_cast<uintptr_t>(z4[k]) | reinterpret_cast<uintptr_t>(r4[k])) & (align - 1))
+            return fail(h, MAS_ERR_ARG, name + ": vector " + std::to_string(k) + " must be " +
+                                            std::to_string(align) + "-byte aligned");
+    }
+    for (int k = 0; k < count; ++k)
+        for (int j = 0; j < count; ++j) {
+            if (j != k && z4[k] == z4[j])
+                return fail(h, MAS_ERR_ARG, name + ": z[" + std::to_string(k) + "] is z[" + std::to_string(j) + "]");
+            if (z4[k] == r4[j])
+                return fail(h, MAS_ERR_ARG, name + ": z[" + std::to_string(k) + "] is r[" + std::to_string(j) + "]");
+        }
+    return MAS_OK;
+}
+
+int mas_apply_multi_device(mas_handle h, int count, float* const* d_z4, const float* const* d_r4, void* stream) {
+    if (!h) return MAS_ERR_ARG;
+    MAS_TRY(check_multi(h, "mas_apply_multi_device", count, d_z4, d_r4, 16));
+    if (!h->prepared) return fail(h, MAS_ERR_STATE, "apply before prepare");
+    MAS_TRY(pending_giveup(h));  // an earlier single apply's incomplete z, as mas_apply_device
+    if (h->fineBlk0 != 0 || h->fineBlk1 != h->nFineBlk)
+        return fail(h, MAS_ERR_STATE, "apply: the handle was prepared for one shard (mas_set_prepare_shard); "
+                                      "use the sharded apply of that shard");
+    hipSetDevice(h->device);
+    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+    if (count == 1)
+        return run_apply(h, reinterpret_cast<float4*>(d_z4[0]), reinterpret_cast<const float4*>(d_r4[0]), s);
+    return run_apply_multi(h, count, reinterpret_cast<float4* const*>(d_z4),
+                           reinterpret_cast<const float4* const*>(d_r4), s);
+}
+
+int mas_apply_multi(mas_handle h, int count, float* const* z4, const float* const* r4) {
+    if (!h) return MAS_ERR_ARG;
+    MAS_TRY(check_multi(h, "mas_apply_multi", count, z4, r4, 4));
+    if (!h->prepared) return fail(h, MAS_ERR_STATE, "apply before prepare");
+    hipSetDevice(h->device);
+    // staged through count x nV x 16 bytes each way; plain pageable copies (the
+    // host_register slots belong to mas_apply's single r and z)
+    const size_t bytes = (size_t)h->nV * 16;
+    MAS_TRY(ensure(h, h->rStage, count * bytes));
+    MAS_TRY(ensure(h, h->zStage, count * bytes));
+    float* dz[MAS_MAX_RHS];
+    const float* dr[MAS_MAX_RHS];
+    for (int k = 0; k < count; ++k) {
+        dr[k] = P<float>(h->rStage) + (size_t)k * h->nV * 4;
+        dz[k] = P<float>(h->zStage) + (size_t)k * h->nV * 4;
+        MAS_TRY(hip_check(h, hipMemcpyAsync(const_cast<float*>(dr[k]), r4[k], bytes, hipMemcpyHostToDevice, h->stream),
+                          "H2D r"));
+    }
+    MAS_TRY(mas_apply_multi_device(h, count, dz, dr, h->stream));
+    for (int k = 0; k < count; ++k)
+        MAS_TRY(hip_check(h, hipMemcpyAsync(z4[k], dz[k], bytes, hipMemcpyDeviceToHost, h->stream), "D2H z"));
+    MAS_TRY(hip_check(h, hipStreamSynchronize(h->stream), "apply sync"));
+    return pending_giveup(h);  // count == 1 runs the single path: its own incomplete z
+}
+
 int mas_pcg_solve_device(mas_handle h, const float* d_diag9, const float* d_off9, const int* d_ranges, float* d_x4,
                          const float* d_b4, int max_iters, float tol, int precondition, mas_pcg_result* out,
                          void* stream) {

@@ -325,6 +325,10 @@ struct mas_context {
     mas::Buffer caCnt, caOff, caKeys, caKeysS, caIds, caIdsS, caVal;
     mas::Buffer cpCnt, cpOff, cpKeys, cpKeysS, cpIds, cpIdsS;
     mas::Buffer Rc, Zc, members, coarseMask, shardOff, shardPos1, l1src;
+    // multi-vector apply (k_multi.hip): one slab of the coarse node range per
+    // vector of the batch, grown by the first call at a given count; the
+    // single-vector Rc / Zc are never touched by it
+    mas::Buffer RcMulti, ZcMulti;
     mas::Buffer splitDev, prepSeg, prepGathered, splitPartsDev;  // coarse split: bounds + flag, segments, part table
     // Incremental level maps (DESIGN.md section 4 "Prepare").
     // The contact-free ("mesh") hierarchy of the current sort is built once and
@@ -454,7 +458,7 @@ struct mas_context {
                               &tab, &termCnt,
                               &cdCnt, &cdOff, &cdKeys, &cdKeysS, &cdIds, &cdIdsS, &cdVal, &cFineOff, &cdEnt, &c0Ent, &caCnt, &caOff,
                               &caKeys, &caKeysS, &caIds, &caIdsS, &caVal, &cpCnt, &cpOff, &cpKeys, &cpKeysS, &cpIds,
-                              &cpIdsS, &Rc, &Zc, &splitDev, &prepSeg, &prepGathered, &splitPartsDev, &members, &coarseMask, &shardOff, &shardPos1, &l1src, &deepKeys, &deepVals, &deepIdx, &deepOff, &deepPos, &deepR1, &deepCnt, &deepIdxShard, &c1Tags, &l1info, &pcgVec, &pcgPartial, &pcgState, &pcgStage, &pcgEllOff, &pcgEllIdx, &pcgEllCnt, &pcgRzPart, &shardSeg, &shardGathered, &diagStage, &offStage, &rangeStage, &rStage, &zStage,
+                              &cpIdsS, &Rc, &Zc, &RcMulti, &ZcMulti, &splitDev, &prepSeg, &prepGathered, &splitPartsDev, &members, &coarseMask, &shardOff, &shardPos1, &l1src, &deepKeys, &deepVals, &deepIdx, &deepOff, &deepPos, &deepR1, &deepCnt, &deepIdxShard, &c1Tags, &l1info, &pcgVec, &pcgPartial, &pcgState, &pcgStage, &pcgEllOff, &pcgEllIdx, &pcgEllCnt, &pcgRzPart, &shardSeg, &shardGathered, &diagStage, &offStage, &rangeStage, &rStage, &zStage,
                               &cubTemp, &rsKeys, &rsVals, &rsHist, &rsPart, &rsKeysP, &rsValsP, &rsHistP, &rsPartP, &add0, &c0Cnt, &c0Off, &c0Keys, &c0KeysS, &c0Ids, &c0IdsS,
                               &c0Val, &a0Keys, &a0KeysS, &a0Ids, &a0IdsS, &a0Val,
                               &spCst, &spGn, &spVmap, &spCoarseTables, &spFine, &spCoarseMask, &hierFlags, &recRanges,
@@ -543,7 +547,8 @@ void launch_coarse_one(mas_context* h, const float4* r, hipStream_t s);  // k_co
 int build_coarse1_tables(mas_context* h, hipStream_t s);
 bool coarse1_supported(const mas_context* h);  // the tag slots exist (k_coarse1.hip)
 void launch_coarse_levels(mas_context* h, int lFirst, const float4* d_r, hipStream_t s);
-void launch_coarse_deep(mas_context* h, const float4* src, const int* idx, hipStream_t s);
+void launch_coarse_deep(mas_context* h, const float4* src, const int* idx, hipStream_t s, float4* rc = nullptr,
+                        float4* zc = nullptr);
 int deep_nodes(const mas_context* h);  // level-3 node ids incl. padding (0 below L = 4)
 mas::DeepArgs deep_args(mas_context* h, const float4* src, const int* idx);
 int build_deep_lists(mas_context* h, hipStream_t s);
@@ -563,6 +568,12 @@ void launch_coarse_apply(mas_context* h, const float4* d_r, hipStream_t s);  // 
 void launch_fine_z0(mas_context* h, int blk0, int blkEnd, const float4* r, float4* z, hipStream_t s);
 void launch_prolong(mas_context* h, int v0, int v1, float4* z, hipStream_t s);
 int fine_grid(const mas_context* h);  // workgroups of one fine launch over every level-0 block
+// the fine launch form (cache policy of the inverse loads) for nb level-0 blocks and nvec vectors (k_apply.hip)
+int fine_var(const mas_context* h, int nb, int nvec = 1);
+// k_multi.hip: count (2 .. MAS_MAX_RHS) applies of one prepared handle in one
+// pass over the inverses; z[k] bitwise run_apply(z[k], r[k]).  The pointers are
+// checked by the caller (mas_apply_multi_device).
+int run_apply_multi(mas_context* h, int count, float4* const* d_z, const float4* const* d_r, hipStream_t s);
 int compute_l1_first(mas_context* h, hipStream_t s);
 // up to 8 device ints -> out, through pinned memory (mas_capi.hip)
 int read_back(mas_context* h, hipStream_t s, std::initializer_list<const int*> src, int* out);

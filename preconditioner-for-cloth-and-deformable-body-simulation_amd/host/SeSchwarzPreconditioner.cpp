@@ -64,4 +64,31 @@ void SeSchwarzPreconditioner::PreconditioningDevice(SeVec3fSimd* z, const SeVec3
           "PreconditioningDevice");
 }
 
+namespace {
+// the C ABI's float pointers from the facade's SeVec3fSimd pointers (a count out
+// of range is left for the C ABI to refuse)
+struct MultiPtrs {
+    float* z[MAS_MAX_RHS] = {};
+    const float* r[MAS_MAX_RHS] = {};
+    MultiPtrs(SeVec3fSimd* const* zz, const SeVec3fSimd* const* rr, int count) {
+        for (int k = 0; zz && rr && k < count && k < MAS_MAX_RHS; ++k) {
+            z[k] = reinterpret_cast<float*>(zz[k]);
+            r[k] = reinterpret_cast<const float*>(rr[k]);
+        }
+    }
+};
+}  // namespace
+
+void SeSchwarzPreconditioner::PreconditioningMulti(SeVec3fSimd* const* z, const SeVec3fSimd* const* residual,
+                                                   int count, int /*dim*/) {
+    const MultiPtrs p(z, residual, count);
+    Check(mas_apply_multi(m_handle, count, p.z, p.r), "PreconditioningMulti");
+}
+
+void SeSchwarzPreconditioner::PreconditioningDeviceMulti(SeVec3fSimd* const* z, const SeVec3fSimd* const* residual,
+                                                         int count, void* stream) {
+    const MultiPtrs p(z, residual, count);
+    Check(mas_apply_multi_device(m_handle, count, p.z, p.r, stream), "PreconditioningDeviceMulti");
+}
+
 }  // namespace SE

@@ -8,6 +8,7 @@ Mirrors the reference plugin surface (SeSchwarzPreconditioner.h:37-178):
     P.PreparePreconditioner(diag, off, ranges, ef, ee, vf, efC, eeC, vfC)
     z = P.Preconditioning(None, r, 3 * nV)        # host arrays
     P.PreconditioningDevice(z_dev, r_dev, stream) # torch cuda tensors / raw pointers
+    P.PreconditioningDeviceMulti(z[K], r[K], stream)  # K <= 8 residuals, one pass over the inverses
 
 The shared library is loaded from the package's lib/ directory; there is no
 CPU fallback -- if the HIP library or a GPU is missing every call raises.
@@ -36,7 +37,8 @@ ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, 
 
 # every entry point declared in include/mas_capi.h
 EXPORTS = ["mas_version", "mas_create", "mas_destroy", "mas_last_error", "mas_allocate", "mas_prepare",
-           "mas_prepare_device", "mas_apply", "mas_apply_device", "mas_set_profiling", "mas_profile_fine",
+           "mas_prepare_device", "mas_apply", "mas_apply_device", "mas_apply_multi", "mas_apply_multi_device",
+           "mas_set_profiling", "mas_profile_fine",
            "mas_profile_coarse", "mas_get_info",
            "mas_get_stats", "mas_get_maps", "mas_get_neighbors", "mas_get_block_matrix", "mas_get_block_inverse",
            "mas_get_packed_inverses",
@@ -133,6 +135,8 @@ def lib():
         L.mas_prepare_device.argtypes = [P, P, P, P, P, P, P, P, P, P, P]
         L.mas_apply.argtypes = [P, P, P]
         L.mas_apply_device.argtypes = [P, P, P, P]
+        L.mas_apply_multi_device.argtypes = [P, I, P, P, P]
+        L.mas_apply_multi.argtypes = [P, I, P, P]
         L.mas_set_profiling.argtypes = [P, I]
         L.mas_profile_fine.argtypes = [P, P, P, I, P, ctypes.POINTER(ctypes.c_double)]
         L.mas_profile_coarse.argtypes = [P, P, I, P, ctypes.POINTER(ctypes.c_double)]
@@ -218,6 +222,60 @@ def _dev(t, count, width, dtype_name, name):
     if t.numel() != count * width:
         raise MasError(f"{name}: expected {count} x {width} elements, got shape {tuple(t.shape)}")
     return t
+
+
+MAS_MAX_RHS = 8  # include/mas_capi.h
+
+
+def _dev_multi(t, nV, name, count=None):
+    """Operand of a multi-vector device apply -> list of K device pointers.
+    t: a contiguous torch cuda float32 tensor [K, nV, 4], or a sequence of K
+    [nV, 4] such tensors and / or raw device pointers (ints, trusted).  K must
+    be 1 .. MAS_MAX_RHS, and `count` when given (the other operand's K).  Shape,
+    dtype and layout are checked before the device, so a CPU tensor fails on
+    what is wrong with it first and on being a CPU tensor last."""
+    def tensor(x, shape, what):
+        if str(x.dtype) != "torch.float32":
+            raise MasError(f"{what}: expected torch.float32, got {x.dtype}")
+        if not x.is_contiguous():
+            raise MasError(f"{what}: tensor must be contiguous")
+        if tuple(x.shape[-len(shape):]) != shape:
+            raise MasError(f"{what}: expected trailing shape {shape}, got shape {tuple(x.shape)}")
+        if not x.is_cuda:
+            raise MasError(f"{what}: tensor is not on a GPU")
+
+    if t is None:
+        raise MasError(f"{name}: missing device arrays")
+    if hasattr(t, "data_ptr"):
+        if t.dim() != 3:
+            raise MasError(f"{name}: expected a [K, {nV}, 4] tensor, got shape {tuple(t.shape)}")
+        tensor(t, (nV, 4), name)
+        ptrs = [t.data_ptr() + k * nV * 16 for k in range(t.shape[0])]
+    elif isinstance(t, (list, tuple)):
+        ptrs = []
+        for k, x in enumerate(t):
+            if isinstance(x, int):
+                ptrs.append(x)
+            elif hasattr(x, "data_ptr"):
+                if x.dim() != 2:
+                    raise MasError(f"{name}[{k}]: expected a [{nV}, 4] tensor, got shape {tuple(x.shape)}")
+                tensor(x, (nV, 4), f"{name}[{k}]")
+                ptrs.append(x.data_ptr())
+            else:
+                raise MasError(f"{name}[{k}]: expected a torch cuda tensor or a raw device pointer, "
+                               f"got {type(x).__name__}")
+    else:
+        raise MasError(f"{name}: expected a [K, {nV}, 4] torch cuda tensor or a sequence of tensors / raw "
+                       f"device pointers, got {type(t).__name__}")
+    if not 1 <= len(ptrs) <= MAS_MAX_RHS:
+        raise MasError(f"{name}: MAS_ERR_ARG: 1 .. {MAS_MAX_RHS} vectors expected, got {len(ptrs)}")
+    if count is not None and len(ptrs) != count:
+        raise MasError(f"{name}: MAS_ERR_ARG: {len(ptrs)} vectors, the other operand has {count}")
+    return ptrs
+
+
+def _ptr_array(ptrs):
+    return (ctypes.c_void_p * len(ptrs))(*ptrs)
 
 
 class SeSchwarzPreconditioner:
@@ -346,6 +404,44 @@ class SeSchwarzPreconditioner:
         z = _dev(z, self._nV, 4, "float32", "z")
         residual = _dev(residual, self._nV, 4, "float32", "residual")
         self._check(self._L.mas_apply_device(self.h, _ptr(z), _ptr(residual), _ptr(stream)), "PreconditioningDevice")
+
+    # ---- multi-vector apply (mas_apply_multi*, include/mas_capi.h) ----
+    def PreconditioningDeviceMulti(self, z, residual, stream=None):
+        """K = 1 .. 8 residuals in one pass over the inverses; z[k] is bitwise
+        PreconditioningDevice(z[k], residual[k]).  z, residual: each a contiguous
+        torch cuda float32 tensor [K, nV, 4], or a sequence of K [nV, 4] tensors
+        or raw device pointers.  No z[k] may be another z[j] or any residual[j].
+        The first call at a given K allocates (not inside a stream capture)."""
+        self._need("PreconditioningDeviceMulti")
+        zp = _dev_multi(z, self._nV, "z")
+        rp = _dev_multi(residual, self._nV, "residual", count=len(zp))
+        self._check(self._L.mas_apply_multi_device(self.h, len(zp), _ptr_array(zp), _ptr_array(rp), _ptr(stream)),
+                    "PreconditioningDeviceMulti")
+
+    def PreconditioningMulti(self, z, residual):
+        """Host arrays: residual [K, nV, 4] float32; z the same shape, written
+        in place, or None (allocated).  Returns z; synchronous."""
+        self._need("PreconditioningMulti")
+        nV = self._nV
+        if residual is None or hasattr(residual, "data_ptr"):
+            raise MasError("PreconditioningMulti: residual must be a host array (use PreconditioningDeviceMulti)")
+        r = np.ascontiguousarray(residual, dtype=np.float32)
+        if r.ndim != 3 or r.shape[1:] != (nV, 4):
+            raise MasError(f"PreconditioningMulti: residual: expected [K, {nV}, 4], got shape {r.shape}")
+        K = r.shape[0]
+        if not 1 <= K <= MAS_MAX_RHS:
+            raise MasError(f"PreconditioningMulti: MAS_ERR_ARG: 1 .. {MAS_MAX_RHS} vectors expected, got {K}")
+        if z is None:
+            out = np.empty((K, nV, 4), np.float32)
+        else:  # written in place: must be exactly the C layout
+            if not (isinstance(z, np.ndarray) and z.dtype == np.float32 and z.flags.c_contiguous
+                    and z.flags.writeable and z.shape == r.shape):
+                raise MasError(f"PreconditioningMulti: z must be a writable C-contiguous float32 array {r.shape}")
+            out = z
+        zp = [out.ctypes.data + k * nV * 16 for k in range(K)]
+        rp = [r.ctypes.data + k * nV * 16 for k in range(K)]
+        self._check(self._L.mas_apply_multi(self.h, K, _ptr_array(zp), _ptr_array(rp)), "PreconditioningMulti")
+        return out
 
     # ---- the sharded coarse assembly (include/mas_capi.h, ABI 5) ----
     def prepare_shard_rows(self):
